@@ -4,6 +4,7 @@ bench.py -- ELBO evals/sec of the movielens model at K=30 on MI355X (BASELINE.js
 HBM-roofline fraction of the dominant reduce_Ks kernel and the CPU baseline timed on the same box.
 
     python bench.py --gpus 1 --steps 50 --warmup 5
+    python bench.py --gpus 1 --steps 50 --warmup 5 --dump-outputs DIR     (+ the last step's ELBO as DIR/elbo.npy)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -394,6 +395,14 @@ def self_launch(args):
     return subprocess.call(cmd, env=env)
 
 
+def dump_outputs(path, elbo):
+    """--dump-outputs: what the timed path returned in its last step -- the ELBO of the last timed evaluation (an fp32
+    scalar; float64 holds it exactly) -- as <path>/elbo.npy, so that two builds can be compared on the same inputs."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "elbo.npy"), np.asarray(elbo, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -404,6 +413,8 @@ def main():
     ap.add_argument("--c4-only", action="store_true", help="of the extras, only the C4 (movielens K=100) figure")
     ap.add_argument("--eager", action="store_true",
                     help="launch every kernel from Python each step instead of replaying a HIP graph")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the last timed evaluation's ELBO to DIR/elbo.npy (float64)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -476,6 +487,8 @@ def main():
     else:
         dt, elbo = timed_evals(sample, strat, args.steps, args.warmup, world, timer=kt)
     res = kt.results()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, elbo)
 
     out = {
         "metric": "ELBO evals/sec at K=30 (movielens)" if K == 30 else f"ELBO evals/sec at K={K} (movielens)",

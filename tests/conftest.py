@@ -1,6 +1,11 @@
 import os
 import sys
 
+# MKL (torch-CPU exp / log / matmul) picks its code path by CPU model, and the paths differ in the last bit.  Pin the
+# processor-independent one -- the path the golden fixtures were recorded on (tests/golden/make_golden.py) -- so that the
+# oracle's bitwise and tight checks give the same answer on every x86 host.  (Set before torch loads MKL.)
+os.environ["MKL_CBWR"] = "COMPATIBLE"
+
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
