@@ -953,7 +953,6 @@ static int chain_run(const void *ms_, int64_t B, int64_t Tn, int64_t K, int64_t 
     if (!ws || ws_bytes < tl.bytes) return ALAN_ERR_WORKSPACE;
     const T *src = (const T *)ms_;
     int64_t cB = sB, cT = sT, cR = sRow, cC = sCol;
-    static const bool no_wave = env_knob("ALAN_CHAIN_WAVE") == 0;                     // ablation: chain_tree_kernel instead
     bool fits32 = true;                                   // the wave kernel's 32-bit offsets inside one matrix
     {
         auto span = [&](int64_t r, int64_t c) { return ((r < 0 ? -r : r) + (c < 0 ? -c : c)) * (K - 1) < (1ll << 31) - 1; };
@@ -966,7 +965,7 @@ static int chain_run(const void *ms_, int64_t B, int64_t Tn, int64_t K, int64_t 
                      ad0.nvs[2] == 0 && ad0.nls[3] == 0 && (!ad0.nl0 || (span(ad0.nl0s[2], 0) && ad0.nl0s[3] == 0));
     }
     // (below K ~ 12 the vector-unit tree kernel is as fast or faster: a 32 x 32 MFMA tile is mostly padding there)
-    if (K > 12 && K <= 32 && !no_wave && fits32 && std::is_same<T, float>::value) {
+    if (K > 12 && K <= 32 && fits32 && std::is_same<T, float>::value) {
         const size_t wsmem = (size_t)(25 * WAVE_TILE + 16 * 32) * sizeof(float);     // the largest launch (5 rounds)
         for (auto fn : {(const void *)chain_wave_kernel<0>, (const void *)chain_wave_kernel<1>, (const void *)chain_wave_kernel<2>,
                         (const void *)chain_wave_kernel<0, true, 256>, (const void *)chain_wave_kernel<1, true, 256>,
@@ -1043,13 +1042,11 @@ static int chain_run(const void *ms_, int64_t B, int64_t Tn, int64_t K, int64_t 
             cC = 1;
         }
     } else {
-        constexpr bool no_mfma = false;
         for (int r = 1; r <= tl.L; ++r) {
             T *dst = (T *)((char *)ws + tl.off[r]);
-            int rc = no_mfma ? (int)ALAN_ERR_UNSUPPORTED
-                             : launch_pair_mfma<T>(K, (uint32_t)tl.n[r], (uint32_t)B, stream, src, cB, cT, cR, cC,
-                                                   (int)tl.n[r - 1], dst, r == tl.L ? (T *)out_vec : (T *)nullptr,
-                                                   r == 1 ? ad0 : none);
+            int rc = launch_pair_mfma<T>(K, (uint32_t)tl.n[r], (uint32_t)B, stream, src, cB, cT, cR, cC,
+                                         (int)tl.n[r - 1], dst, r == tl.L ? (T *)out_vec : (T *)nullptr,
+                                         r == 1 ? ad0 : none);
             if (rc == ALAN_ERR_LAUNCH) return rc;
             if (rc == ALAN_ERR_UNSUPPORTED) {
                 ALAN_LAUNCH(kern, dim3((uint32_t)tl.n[r], (uint32_t)B), dim3(CHAIN_THREADS), smem, stream, src, cB,
@@ -1732,12 +1729,11 @@ static int chain_backward_run(const void *ms, int64_t B, int64_t Tn, int64_t K, 
     const TreeLayout tl = tree_layout(B, Tn, K, sizeof(T));
     if (tl.L > 1 && (!ws || ws_bytes < tl.bytes)) return ALAN_ERR_WORKSPACE;
     auto kern = K <= 48 ? chain_pair_backward_kernel<T, 2> : chain_pair_backward_kernel<T, 4>;
-    static const int bwd_mfma_knob = env_knob("ALAN_CHAIN_BWD_MFMA");                 // ablation knob: 0 = the vector kernel
     bool mfma = false;
     size_t smem_m = 0;
     if constexpr (sizeof(T) == 4) {
         smem_m = (3 * (size_t)K * (size_t)(K | 1) + 6 * (size_t)K) * sizeof(float);
-        mfma = bwd_mfma_knob != 0 && K >= 2 && smem_m <= 160 * 1024;
+        mfma = K >= 2 && smem_m <= 160 * 1024;
         if (mfma && smem_m > 64 * 1024 &&
             hipFuncSetAttribute((const void *)chain_pair_backward_mfma_kernel<1024>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)smem_m) != hipSuccess)
@@ -1748,8 +1744,7 @@ static int chain_backward_run(const void *ms, int64_t B, int64_t Tn, int64_t K, 
             return ALAN_ERR_LAUNCH;
     const T *root = (const T *)((const char *)tree + tl.off[tl.L]);
     if constexpr (sizeof(T) == 4) {
-        static const int tree_knob = env_knob("ALAN_CHAIN_BWD_TREE");                 // ablation knob: 0 = a launch per round
-        if (mfma && tree_knob != 0 && tl.L >= 2 && tl.L <= BWD_MAX_LEVELS) {
+        if (mfma && tl.L >= 2 && tl.L <= BWD_MAX_LEVELS) {
             // one launch for the whole tree (chain_tree_backward_kernel) behind one that marks the workspace as not yet written
             BwdTree a;
             std::memset(&a, 0, sizeof(a));

@@ -11,8 +11,9 @@
 
 namespace alan {
 
-// A tuning / ablation knob from the environment, read ONCE per process (a `static const` at the use site): launch
-// paths never call getenv again, and a later setenv() cannot change the library's behaviour under a running caller.
+// A setting from the environment (ALAN_NLB_X2, normal_lse_bwd.hip), read ONCE per process (a `static const` at the use
+// site): launch paths never call getenv again, and a later setenv() cannot change the library's behaviour under a
+// running caller.
 constexpr int ENV_UNSET = -2147483647 - 1;
 inline int env_knob(const char *name) {
     const char *e = getenv(name);

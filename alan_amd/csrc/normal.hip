@@ -38,9 +38,6 @@ struct NormalDesc {
     int64_t l_os, s_os;               // out strides along the loc / scale dims
     FastDiv vdiv[MAXD];
     int64_t v_vs[MAXD], v_os[MAXD];   // value / out strides over the value's keep dims
-#ifdef ALAN_ABLATE
-    int32_t dbg;                      // ablation knob (ALAN_NORMAL_ABLATE): 1 prologue only, 2 no stores, 3 one scale row
-#endif
 };
 
 // R = value rows per thread (rows t, t+256, ... of the workgroup's block of 256*R): every 16-byte read of a
@@ -138,25 +135,7 @@ __global__ __launch_bounds__(256) void normal_outer_kernel(const NormalDesc d) {
     }
     __syncthreads();
 
-#ifdef ALAN_ABLATE
-    if (d.dbg == 1) {   // ablation: prologue only
-        float q = lg[tid % d.NS];
-#pragma unroll
-        for (int j = 0; j < R; ++j)
-#pragma unroll
-            for (int e = 0; e < EMAX; ++e) q += v[j][e];
-        if (active[0]) d.out[ooff[0] + (int64_t)l0 * d.l_os] = q;
-        return;
-    }
-    const uint32_t ns_run = d.dbg == 3 ? 1u : d.NS;
-    const bool store_on = d.dbg != 2;
-#else
-    const uint32_t ns_run = d.NS;
-    constexpr bool store_on = true;
-#endif
-    bool do_store[R];
-#pragma unroll
-    for (int j = 0; j < R; ++j) do_store[j] = active[j] && store_on;
+    const uint32_t ns = d.NS;
     for (uint32_t il = l0; il < l1; ++il) {
         const float4 *m4 = reinterpret_cast<const float4 *>(mu + (size_t)(il - l0) * Ep);
         float dd[R][EMAX];
@@ -173,7 +152,7 @@ __global__ __launch_bounds__(256) void normal_outer_kernel(const NormalDesc d) {
                 dd[j][4 * q + 3] = e * e;
             }
         }
-        for (uint32_t is = 0; is < ns_run; ++is) {
+        for (uint32_t is = 0; is < ns; ++is) {
             const float4 *w4 = reinterpret_cast<const float4 *>(w + (size_t)is * Ep);
             float4 ww[EMAX / 4];
 #pragma unroll
@@ -190,7 +169,7 @@ __global__ __launch_bounds__(256) void normal_outer_kernel(const NormalDesc d) {
                     acc = fmaf(dd[j][4 * q + 3], ww[q].w, acc);
                 }
                 const float res = (-acc - lgi) * d.out_scale + d.add_const;
-                if (do_store[j] || (!store_on && res == 12345.678f))
+                if (active[j])
                     d.out[ooff[j] + (int64_t)il * d.l_os + (int64_t)is * d.s_os] = res;
             }
         }
@@ -300,15 +279,6 @@ __global__ __launch_bounds__(256) void normal_mfma_kernel(const NormalDesc d) {
         const float x = d.val[voff + min(e, E - 1)];
         z[step] = e < E ? x : 0.f;
     }
-#ifdef ALAN_ABLATE
-    const bool store_on = d.dbg != 2, mfma_on = d.dbg != 4;
-    if (d.dbg == 1) {
-        if (z[0] + wreg[0][0] + cinit[0][0] == 12345.678f) d.out[0] = 1.f;
-        return;
-    }
-#else
-    constexpr bool store_on = true, mfma_on = true;
-#endif
     // Buffer stores: address = descriptor base + (wave-uniform byte offset of the (loc row, scale tile), an SGPR) +
     // (this lane's byte offset, ONE VGPR stepped from scale row to scale row).  With flat stores the compiler kept 16
     // 64-bit row addresses per tile in vector registers (312 VGPRs at NST = 4: one wave per SIMD).  Lanes without a
@@ -331,22 +301,12 @@ __global__ __launch_bounds__(256) void normal_mfma_kernel(const NormalDesc d) {
         }
 #pragma unroll
         for (int st = 0; st < NST; ++st) {
-            f32x16 acc = cinit[st];
-            if (mfma_on) {
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wreg[st][0], dd[0], cinit[st], 0, 0, 0);
+            f32x16 acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wreg[st][0], dd[0], cinit[st], 0, 0, 0);
 #pragma unroll
-                for (int step = 1; step < EH; ++step)
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wreg[st][step], dd[step], acc, 0, 0, 0);
-            } else {
-                acc[0] += dd[0] + dd[EH - 1];
-            }
+            for (int step = 1; step < EH; ++step)
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wreg[st][step], dd[step], acc, 0, 0, 0);
             const uint32_t tile_boff = (uint32_t)((int64_t)il * d.l_os + (int64_t)(32 * st) * d.s_os) * 4u;
-            if (!store_on) {
-                float q = 0.f;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) q += acc[r];
-                if (q == 12345.678f) d.out[0] = q;
-            } else if (TS) {
+            if (TS) {
                 const int rows_ok = (int)d.NS - 4 * h;
                 asm volatile("" ::: "memory");
                 __builtin_amdgcn_wave_barrier();               // the previous tile's reads are issued (LDS is in order)
@@ -395,9 +355,7 @@ static void launch_normal_mfma(int nst, dim3 grid, hipStream_t stream, const EvP
 
 // d is filled except for l_chunk.  Declines (false) outside E <= 32, NS <= 128.
 static bool try_normal_mfma(NormalDesc d, int64_t NV, hipStream_t stream, const EvPair &ev) {
-    static const int mfma_knob = env_knob("ALAN_NORMAL_MFMA");                                   // ablation knob
-    const bool off = mfma_knob == 0;
-    if (off || d.E > 32 || d.NS > 128) return false;
+    if (d.E > 32 || d.NS > 128) return false;
     {   // lanes address the output by a 32-bit element offset from a wave-uniform base
         int64_t span = (int64_t)(d.NL - 1) * d.l_os + (int64_t)(d.NS - 1) * d.s_os;
         for (int k = 0; k < d.nv; ++k) span += (int64_t)(d.vdiv[k].d - 1) * d.v_os[k];
@@ -405,8 +363,7 @@ static bool try_normal_mfma(NormalDesc d, int64_t NV, hipStream_t stream, const 
         d.out_bytes = (uint32_t)((span + 1) * 4);
         // beyond the 256 MiB Infinity Cache the factor streams to HBM, where this kernel's 2 x 128-byte runs per store
         // reach 2.3 TB/s against the vector kernel's 3.0 (K=100 unsplit, 1.2 GB); inside it, 4.2 against 2.9
-        const bool force = mfma_knob == 2;
-        if (d.out_bytes > (224u << 20) && !force) return false;
+        if (d.out_bytes > (224u << 20)) return false;
         for (int k = 0; k < d.nv; ++k)
             if (d.v_os[k] < 0) return false;
     }
@@ -503,10 +460,6 @@ int try_launch_normal_outer(const Canon &c, bool log_scale, float out_scale, dou
     d.log_scale = log_scale ? 1 : 0;
     d.out_scale = out_scale;
     d.add_const = (float)add_const;
-#ifdef ALAN_ABLATE
-    static const int ablate_knob = env_knob("ALAN_NORMAL_ABLATE");
-    if (ablate_knob != ENV_UNSET) d.dbg = ablate_knob;
-#endif
     if (try_normal_mfma(d, NV, stream, ev)) return hipGetLastError() == hipSuccess ? ALAN_OK : ALAN_ERR_LAUNCH;
     {   // value rows contiguous in row-index order?  (voff(r) = r * E)
         bool contig = reinterpret_cast<uintptr_t>(d.val) % 16 == 0;   // (a workgroup's block starts 1 KiB-aligned)

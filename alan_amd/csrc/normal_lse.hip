@@ -464,8 +464,7 @@ int plan_nl(const alan_normal_lse_desc_t &a, NLPlan &p) {
     // the last scale tile as a 16-wide one: a single group of tiles whose last holds at most 16 rows (NS = 100: 4)
     p.rag = p.nst > 1 && nsg == 1 && nst_total == p.nst && a.NS - 32 * (nst_total - 1) <= 16;
     // the bf16x3 kernel (default): contiguous value rows (its staged loads), the chunks added by a second launch
-    static const int f32_knob = env_knob("ALAN_NLSE_F32");                            // ablation knob: 1 = the f32 MFMA kernel
-    p.x3 = a.v_se == 1 && a.v_sk == a.E && f32_knob != 1 &&
+    p.x3 = a.v_se == 1 && a.v_sk == a.E &&
            a.l_sl >= 0 && a.l_se >= 0 && a.s_ss >= 0 && a.s_se >= 0 &&                   // (its 32-bit lane offsets)
            a.NL * a.l_sl + a.E * a.l_se < (1ll << 31) && a.NS * a.s_ss + a.E * a.s_se < (1ll << 31) &&
            a.v_sm >= 0 && a.v_sm < (1ll << 31) && a.NL <= 65535;
@@ -481,9 +480,7 @@ int plan_nl(const alan_normal_lse_desc_t &a, NLPlan &p) {
         // per SIMD has nothing to hide its own latencies behind (668 ns per unit against 2 x 244) -- so as many slices
         // as give at most 512 workgroups.
         const int64_t per = nsg_x * ((a.NL + p.nlw - 1) / p.nlw);
-        static const int blocks_knob_x = env_knob("ALAN_NLSE_BLOCKS");                // tuning knob: target workgroups
-        const int64_t target_x = blocks_knob_x != ENV_UNSET ? std::max(1, blocks_knob_x) : 512;
-        int64_t ncg = std::max<int64_t>(1, target_x / std::max<int64_t>(1, per));
+        int64_t ncg = std::max<int64_t>(1, 512 / std::max<int64_t>(1, per));
         ncg = std::min<int64_t>(ncg, std::min<int64_t>(65535, (a.M + 3) / 4));
         p.n_chunks = (int)ncg;
         p.m_chunk = (int)((a.M + 4 * ncg - 1) / (4 * ncg));       // (the largest slice: what flat row tiling's offset check needs)
@@ -492,27 +489,23 @@ int plan_nl(const alan_normal_lse_desc_t &a, NLPlan &p) {
         return ALAN_OK;
     }
     const int64_t gx = (((a.NL + p.nlw - 1) / p.nlw) * nsg + 3) / 4;
-    int64_t target = 768;                                                    // workgroups (x 4 waves)
-    static const int blocks_knob = env_knob("ALAN_NLSE_BLOCKS");                      // tuning knob
-    if (blocks_knob != ENV_UNSET) target = std::max(1, blocks_knob);
+    const int64_t target = 768;                                              // workgroups (x 4 waves)
     int64_t nch = std::max<int64_t>(1, std::min<int64_t>(a.M, target / std::max<int64_t>(1, gx)));
     nch = std::min<int64_t>(nch, 65535);
     p.m_chunk = (int)((a.M + nch - 1) / nch);
-    if (blocks_knob == ENV_UNSET) {
-        // Balance: workgroups spread evenly over the 256 CUs, so the launch lasts as long as the CU with the most of
-        // them -- ceil(workgroups / 256) x (plate elements per workgroup).  Among the chunkings that keep the chip
-        // between ~2 and ~4 waves per SIMD take the cheapest, fewer workgroups on a tie (K=100, M=75: 475 workgroups of
-        // 4 users instead of 625 of 3 -- 98 against 112 us; M=300 and the K=30 launch keep their measured optimum).
-        const int64_t lo = 450, hi = 1100;
-        int64_t best = -1, best_cost = 0;
-        for (int64_t mc = a.M; mc >= 1; --mc) {
-            const int64_t chunks = (a.M + mc - 1) / mc, wgs = gx * chunks;
-            if (chunks > 65535 || wgs < lo || wgs > hi) continue;
-            const int64_t cost = ((wgs + 255) / 256) * mc;
-            if (best < 0 || cost < best_cost) best = mc, best_cost = cost;
-        }
-        if (best > 0) p.m_chunk = (int)best;
+    // Balance: workgroups spread evenly over the 256 CUs, so the launch lasts as long as the CU with the most of them
+    // -- ceil(workgroups / 256) x (plate elements per workgroup).  Among the chunkings that keep the chip between ~2
+    // and ~4 waves per SIMD take the cheapest, fewer workgroups on a tie (K=100, M=75: 475 workgroups of 4 users
+    // instead of 625 of 3 -- 98 against 112 us; M=300 and the K=30 launch keep their measured optimum).
+    const int64_t lo = 450, hi = 1100;
+    int64_t best = -1, best_cost = 0;
+    for (int64_t mc = a.M; mc >= 1; --mc) {
+        const int64_t chunks = (a.M + mc - 1) / mc, wgs = gx * chunks;
+        if (chunks > 65535 || wgs < lo || wgs > hi) continue;
+        const int64_t cost = ((wgs + 255) / 256) * mc;
+        if (best < 0 || cost < best_cost) best = mc, best_cost = cost;
     }
+    if (best > 0) p.m_chunk = (int)best;
     p.n_chunks = (int)((a.M + p.m_chunk - 1) / p.m_chunk);
     p.part_bytes = (size_t)p.n_chunks * a.NL * a.NS * sizeof(float);
     p.grid = dim3((uint32_t)gx, (uint32_t)p.n_chunks);

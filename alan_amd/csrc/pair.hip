@@ -215,8 +215,6 @@ __global__ __launch_bounds__(256) void pair_sum_kernel(const PairDesc d, const i
 // Is this alan_reduce call a pair contraction worth the tile kernel?  Fills its argument.
 bool pair_prepare(const alan_reduce_desc_t &d, uint32_t keep, uint32_t red, uint32_t plate, PairDesc &pd, dim3 &grid,
                   size_t &lds_bytes) {
-    static const int knob = env_knob("ALAN_PAIR");                                   // ablation knob: 0 = off
-    if (knob == 0) return false;
     const bool bern = d.mode == ALAN_MODE_BERNOULLI_LINEAR;
     if ((d.mode != ALAN_MODE_LSE && !bern) || d.n_factors < 2 || d.n_factors > MAXF) return false;
     if (d.weight.data || d.lse_out.data || d.ring_n || d.out.dtype != ALAN_F32 || !d.out.data) return false;

@@ -53,9 +53,6 @@ struct RowsDesc {
     int64_t lks[MAXD];
     KTensor gen[MAXF];      // general secondary factors: ks over INNER keep dims, rs[0] along the row
     int64_t gen_ps[MAXF];
-#ifdef ALAN_ABLATE
-    int32_t dbg;            // ablation knob (ALAN_ROWS_ABLATE): 1 = no reduction, 2 = no global loads
-#endif
 };
 
 #ifndef ROWS_NT
@@ -75,9 +72,6 @@ __global__ __launch_bounds__(256, 4) void rows_kernel(const RowsDesc d) {
     constexpr int NS = SHORT ? 8 : 16;   // float2 slots per lane: a lane holds <= 32 (SHORT: 16) row elements
     const int t = threadIdx.x;
     const int L = d.L;
-#ifdef ALAN_ABLATE
-    if (d.dbg == 4) return;
-#endif
     const uint32_t o0 = blockIdx.x * (uint32_t)d.RB;
     const uint32_t nrows = min((uint32_t)d.RB, d.NO - o0);
     const uint32_t p0 = blockIdx.y * d.p_chunk;
@@ -123,9 +117,6 @@ __global__ __launch_bounds__(256, 4) void rows_kernel(const RowsDesc d) {
         const int64_t a0 = e0 & ~(int64_t)3;
         const int n4 = ((int)(e0 - a0) + (int)nrows * L + 3) >> 2;
         const f32x4 *src = reinterpret_cast<const f32x4 *>(d.F + a0);
-#ifdef ALAN_ABLATE
-        if (d.dbg >= 2) return;
-#endif
         if (a0 + 4 * (int64_t)n4 <= d.total) {  // whole slab inside the tensor (all but the very last one)
 #pragma unroll
             for (int u = 0; u < ROWS_UNR; ++u) {
@@ -280,11 +271,6 @@ __global__ __launch_bounds__(256, 4) void rows_kernel(const RowsDesc d) {
             }
         }
         float val;
-#ifdef ALAN_ABLATE
-        if (d.dbg == 1 || d.dbg == 3) {
-            val = x[0];
-        } else
-#endif
         if (MODE == ALAN_MODE_LSE) {
             float m = NEG;   // exact row max, then sum exp(x - max): the reference's two-pass arithmetic
 #pragma unroll
@@ -375,9 +361,7 @@ RowsPlan plan_rows(const Canon &c, int mode, int compute_dtype) {
     rp.n_windows = (rp.NO + rbmax - 1) / rbmax;
     rp.RB = (int)((rp.NO + rp.n_windows - 1) / rp.n_windows);
     rp.threads = 256;
-    uint32_t target_blocks = 4096;
-    static const int blocks_knob = env_knob("ALAN_ROWS_BLOCKS");                                       // tuning knob
-    if (blocks_knob != ENV_UNSET) target_blocks = (uint32_t)std::max(1, blocks_knob);
+    const uint32_t target_blocks = 4096;
     uint32_t nch = std::max(1u, std::min(rp.P, target_blocks / std::max(1u, rp.n_windows)));
     rp.p_chunk = (rp.P + nch - 1) / nch;
     rp.n_chunks = (rp.P + rp.p_chunk - 1) / rp.p_chunk;
@@ -448,10 +432,6 @@ int launch_rows(const Canon &c, const RowsPlan &rp, int mode, double add_const, 
     for (int j = 0; j < d.nki; ++j) d.lks[j] = c.l.ks[k0 + j];
     d.l_ps = k0 ? c.l.ks[0] : 0;
     d.add_const = two_stage ? 0.f : (float)add_const;
-#ifdef ALAN_ABLATE
-    static const int ablate_knob = env_knob("ALAN_ROWS_ABLATE");
-    if (ablate_knob != ENV_UNSET) d.dbg = ablate_knob;
-#endif
 
     const dim3 grid(rp.n_windows, rp.n_chunks);
     const dim3 block(256);

@@ -147,11 +147,6 @@ def stale_grad_accumulators(params):
     return held
 
 
-_UNSAFE_SKIP_STALE_CHECK = False
-"""Debugging only (tools/graphed_step_crash_probe.py, one recorded run: profiles/r3_graphed_step_crash.txt): with it set,
-constructing a GraphedStep over a live autograd graph is known to end in SIGSEGV inside hipStreamEndCapture."""
-
-
 class GraphedStep:
     """``step = GraphedStep(problem, K, optimizer, method="vi"); elbo = step()``.
 
@@ -180,7 +175,7 @@ class GraphedStep:
         self.problem, self.K, self.opt, self.method = problem, K, optimizer, method
         self.strategy = computation_strategy
         held = stale_grad_accumulators(problem.parameters())
-        if held and not _UNSAFE_SKIP_STALE_CHECK:
+        if held:
             raise RuntimeError(_STALE_MSG + f"  (parameters: {len(held)})")
         side = t.cuda.Stream()
         side.wait_stream(t.cuda.current_stream())
@@ -200,7 +195,7 @@ class GraphedStep:
         for w in seen:
             if w not in stale:
                 warnings.warn_explicit(w.message, w.category, w.filename, w.lineno)
-        if stale and not _UNSAFE_SKIP_STALE_CHECK:
+        if stale:
             # (second net, by torch's own stream-mismatch warning during the warm-up: the structural check above is the
             # guard proper and does not depend on this text)
             raise RuntimeError(_STALE_MSG)

@@ -807,8 +807,7 @@ def test_result_ring_c_abi_delivers_to_successive_slots_and_declines_other_shape
 def test_pair_contraction_against_the_oracle(shape, monkeypatch):
     """out[y, g, k] = sum_b LSE_a(L[y,b,g,a] + q[y,b,a] + P[y,b,k,a]): the output is bigger than every factor, the tile
     kernel of pair.hip takes it (>= 2^20 (output, a) pairs) -- against the oracle's logsumexp_sum + plate_sum, incl. -inf
-    entries and a wholly -inf row (NaN, utils.py:219), and against the generic kernels (ALAN_PAIR=0 is read once per
-    process, so those run in the same call only for sizes the tile kernel declines)."""
+    entries and a wholly -inf row (NaN, utils.py:219)."""
     g = t.Generator().manual_seed(7)
     Y, B, G, A, Ky = (shape[k] for k in ("Y", "B", "G", "A", "Ky"))
     L = t.randn(Y, B, G, A, generator=g) * 3
